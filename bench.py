@@ -2,7 +2,7 @@
 """bench.py -- BASELINE.json's metric on MI355X: Lanczos iterations/s (+ achieved HBM GB/s) for
 eigsolve(Lanczos) on the 10M-row 5-point Laplacian (SparseMatrixCSC), krylovdim = 100.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   N > 1: one rank per GPU.  Launched either by `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`
   (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) or from a plain shell -- then bench.py re-executes
   itself under torch.distributed.run on 127.0.0.1.  The data path has no torch in it: libkrylov_hip owns the RCCL
@@ -377,6 +377,34 @@ def self_launch(args, script=None) -> int:
     return subprocess.call(cmd, env=env)
 
 
+DUMP_ROWS = 32768    # rows of every vector --dump-outputs writes, over all ranks: <= 128 vectors x 32768 rows x 8 bytes = 32 MB
+
+
+def dump_outputs(out_dir: str, config: str, fact, rank: int, world: int):
+    """--dump-outputs: the factorization the last timed step handed to its caller, as float64 DIR/<name>.npy (one file set per
+    rank, suffix .rank<r>, when N > 1).  Scalars in full; every basis / residual vector as the same seeded sample of its rows
+    (the full basis is gigabytes), so that two builds run with the same arguments can be compared output for output."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+
+    def sample(basis, first, count):
+        idx = np.sort(np.random.default_rng(2024).choice(basis.n, size=min(basis.n, DUMP_ROWS // world), replace=False))
+        return np.stack([basis.download(first + j)[idx] for j in range(count)], axis=1)
+
+    if config == "lanczos":
+        arrs = {"alphas": fact.alphas, "betas": fact.betas, "basis": sample(fact.V, fact.window, len(fact.V)),
+                "residual": sample(fact.V, fact.r.col, 1)[:, 0]}
+    elif config == "gkl":
+        arrs = {"alphas": fact.alphas, "betas": fact.betas, "basis_U": sample(fact.U, 0, len(fact.U)),
+                "basis_V": sample(fact.V, 0, len(fact.V)), "residual": sample(fact.U, fact.r.col, 1)[:, 0]}
+    else:
+        arrs = {"H": fact.H[:fact.k, :fact.k], "normres": [fact.normres], "basis": sample(fact.V, 0, fact.k),
+                "residual": sample(fact.V, fact.r_col, fact.R_size)}
+    sfx = f".rank{rank}" if world > 1 else ""
+    for name, a in arrs.items():
+        np.save(d / f"{name}{sfx}.npy", np.asarray(a, dtype=np.float64))
+
+
 # ------------------------------------------------------------------------------------------------ workloads
 def gkl_rows(m_total: int, n: int, per: int, r0: int, r1: int):
     """Rows [r0, r1) of the config-4 map: 5M x 1M sparse random, 20 entries per row (duplicates summed).  Generated in
@@ -426,7 +454,12 @@ def main():
                     help="kk_ctx_set_option before the workload is built (A/B runs; every override is reported in the line as `options_overridden`)")
     ap.add_argument("--ny", type=int, default=NY, help="grid rows per GPU (default 2500 -> 10M rows per GPU)")
     ap.add_argument("--deadline", type=float, default=900.0, help="multi-rank runs only: abort if the whole run takes longer (seconds)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64; vectors as a fixed, "
+                         "seeded sample of their rows)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -722,6 +755,8 @@ def main():
     elapsed = time.perf_counter() - t0
     ctx.prof_enable(0)
     stats1 = comm.stats() if comm else None
+    if args.dump_outputs:        # before any later sweep reuses the basis slab
+        dump_outputs(args.dump_outputs, args.config, fact, rank, world)
     ranks_agree = None
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64)

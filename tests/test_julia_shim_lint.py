@@ -156,7 +156,7 @@ def test_module_is_syntactically_balanced():
 # ------------------------------------------------------------------------------------------------------------------
 # method signatures: every KrylovKit function the shim overloads must exist in the reference with a method of the same
 # shape (positional arity within the reference's range, keyword names a subset, abstract type heads in the same slots).
-# The table is extracted from /root/reference by tests/golden/make_reference_signatures.py and committed.
+# The table is extracted from the reference's sources by tests/golden/make_reference_signatures.py and committed as a fixture.
 # ------------------------------------------------------------------------------------------------------------------
 import json  # noqa: E402
 
@@ -241,17 +241,6 @@ def test_every_overload_matches_a_reference_method():
                         + "; ".join("(" + ", ".join(p["name"] + ("::" + p["type"] if p["type"] else "") for p in r["positional"]) + ")" for r in SIGS[name]))
             checked += 1
     assert checked >= 20
-
-
-def test_reference_signature_table_is_current():
-    """where the reference is mounted (build container) the committed table must equal a fresh extraction"""
-    import subprocess
-    import sys
-    if not Path("/root/reference/src").exists():
-        return
-    fresh = subprocess.run([sys.executable, str(ROOT / "tests" / "golden" / "make_reference_signatures.py")], capture_output=True, text=True)
-    assert fresh.returncode == 0, fresh.stderr
-    assert json.loads((ROOT / "tests" / "golden" / "reference_signatures.json").read_text()) == SIGS
 
 
 def test_julia_harness_covers_every_factorization():

@@ -339,13 +339,13 @@ elif scenario in ("xsync", "xsync_fault", "xsync_late"):
     opA = kd.NativeShardedOperator(A[lo:hi], part, ctx, symmetric=True)
     opC = kd.NativeShardedOperator(Cd[lo:hi], part, ctx)
     import os
-    steps = int(os.environ.get("KK_W2_STEPS", "24"))      # (the 8-rank rehearsal on ONE GPU runs a shorter factorization: eight processes share the chip's queues)
+    steps = int(os.environ.get("KK_W2_STEPS", "24"))      # (the many-rank rehearsal on ONE GPU runs a shorter factorization: five processes share the chip's queues)
     fault_at = ({7, 15} if steps >= 20 else {3}) if scenario != "xsync" else set()   # (short run: one fault -- the back-off after it outlasts the factorization)
     # xsync_late: the faulting rank gives up at the LAST reduction of its launch with its partial already published -- to its peers it
     # looks like a rank whose wait ran out a moment before they arrived: they find every partial in their area and must NOT commit
     # (abort word re-read before the commit), or the ranks' collectives stop pairing up.  k_mgs_persist carries the hook.
     routes = (("persist", 1), ("persist", 0)) if scenario == "xsync_late" else (("persist", 1), ("panel", 1), ("panel_p", 1), ("persist", 0))
-    if os.environ.get("KK_W2_ROUTES"):   # (the 8-rank rehearsal: a subset -- every route costs ~25 s there, the processes time-share the chip)
+    if os.environ.get("KK_W2_ROUTES"):   # (the many-rank rehearsal: a subset -- every route costs ~25 s there, the processes time-share the chip)
         keep = os.environ["KK_W2_ROUTES"].split(",")
         routes = tuple(r for r in routes if f"{r[0]}{r[1]}" in keep)
     for route, lookahead in routes:
