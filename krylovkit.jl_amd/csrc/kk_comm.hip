@@ -102,7 +102,7 @@ KK_API int kk_comm_get_unique_id(void* id128) {
 // same on every rank whatever happens locally.
 // ------------------------------------------------------------------------------------------
 namespace {
-struct xs_record {            // what a rank tells the others (16 x 8 bytes)
+struct xs_record {            // what a rank tells the others (17 x 8 bytes)
     int64_t ok, pid, dev, ptr;
     int64_t bus;              // hash of the PCI bus id of the rank's device: ranks that SHARE a GPU find each other by it
     int64_t cus, dev_cus, xcds;   // CUs the rank's context counts on ("num_cus"), CUs and XCDs of its device

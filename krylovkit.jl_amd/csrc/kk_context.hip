@@ -377,6 +377,9 @@ KK_API int kk_ctx_get_option(kk_ctx c, const char* key, double* value) {
     else if (!strcmp(key, "fstep_threads")) *value = c->fstep_threads;
     else if (!strcmp(key, "fstep_launches")) *value = (double)c->fstep_launches;
     else if (!strcmp(key, "fstep_failures")) *value = (double)c->fstep_failures;
+    else if (!strcmp(key, "fstep_last_blocks")) *value = c->fstep_last_blocks;
+    else if (!strcmp(key, "fstep_last_np")) *value = c->fstep_last_np;
+    else if (!strcmp(key, "fstep_last_threads")) *value = c->fstep_last_threads;
     else if (!strcmp(key, "spmv_dia_sw")) *value = c->spmv_dia_sw;
     else if (!strcmp(key, "spmv_dia_sw_lines")) *value = c->spmv_dia_sw_lines;
     else if (!strcmp(key, "spmv_dia_sw_launches")) *value = (double)c->spmv_dia_sw_launches;

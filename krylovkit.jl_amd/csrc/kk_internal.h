@@ -20,7 +20,7 @@
 #define KK_SYNC_ERR_OFFSET (2 * KK_SYNC_MAX_BLOCKS * KK_SYNC_LINE)
 #define KK_SYNC_BYTES (KK_SYNC_ERR_OFFSET + 64)
 // one-launch Lanczos step of short vectors (kk_kernels_fstep.hip): at most KK_FS_MAX_M basis vectors, at most KK_FS_MAX_BLOCKS blocks of 256 threads
-// x up to 8 row pairs (64 blocks, the default: 262 144 rows); granule area = (2 m + 1 values + the norm) x blocks x 16 bytes, error flag behind it
+// x up to 8 row pairs (128 blocks, the default: 262 144 rows); granule area = (2 m + 1 values + the norm) x blocks x 16 bytes, error flag behind it
 #define KK_FS_MAX_M 128
 #define KK_FS_MAX_BLOCKS 128
 #define KK_FS_SET_BYTES ((2 * KK_FS_MAX_M + 2) * KK_FS_MAX_BLOCKS * 16)   // one granule set; two sets: the two passes of an Arnoldi CGS2 / MGS2 step alternate
@@ -289,6 +289,7 @@ struct kk_ctx_s {
     double fs_token = 0;             // token counter: a launch that committed stores its token into the pinned host slot
     int fstep_fault = 0;             // test hook (option "fstep_fault"): the next N launches give up at once
     int64_t fstep_launches = 0, fstep_failures = 0;   // diagnostics; a failure (launch that did not commit) switches the route off for the context
+    int fstep_last_blocks = 0, fstep_last_np = 0, fstep_last_threads = 0;   // diagnostics: grid, row pairs per thread and block size of the last launch
     int fold_scale = 1;          // persistent kernel stores r / |r| at its commit when an expand! ends with it (no scale pass in the next step)
     int fuse_passes = 1;         // fuse unproject(pass i) with project(pass i+1)
     int speculate = 1;           // enqueue the next expand's SpMV before syncing the host

@@ -343,7 +343,9 @@ __global__ __launch_bounds__(TPB) void k_lanczos_fstep(const int32_t* __restrict
             ws_scal[SC_ALPHA0] = a0; ws_scal[SC_NRM2] = n2; ws_scal[SC_NRM] = rt; ws_scal[SC_INVNRM] = inv; ws_scal[SC_XS] = scale ? 1.0 : inv;
         }
         // host slot: [0] token (written LAST), [1] alpha0, [2] last coefficient before the fold, [3 .. 5] |w|^2, |w|, 1 / |w|, [6] stored normalised?,
-        // [8 .. 8 + m) the Gram row g = V'v.  System-scope stores; the token follows a system-scope fence.
+        // [8 .. 8 + m) the Gram row g = V'v, [8 + KK_FS_MAX_M ..) the coefficients.  System-scope stores by thread i (row i: waves 1 .. 3 too once
+        // m > 64); EVERY thread that stored issues a system-scope release fence before the barrier -- the barrier itself is only a workgroup-scope
+        // fence, so tid 0's release alone would not order the other waves' stores before the token
         for (int i = tid; i < m; i += TPB) { fs_host_store(host_out + 8 + i, gsave[i]); fs_host_store(host_out + 8 + KK_FS_MAX_M + i, hsum[i]); }
         if (tid == 0) {
             fs_host_store(host_out + 1, a0);
@@ -353,11 +355,10 @@ __global__ __launch_bounds__(TPB) void k_lanczos_fstep(const int32_t* __restrict
             fs_host_store(host_out + 5, inv);
             fs_host_store(host_out + 6, scale ? 1.0 : 0.0);
         }
+        if (tid < m || tid == 0) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");   // system scope
         __syncthreads();
-        if (tid == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");   // system scope: every store above is visible to the host before the token
+        if (tid == 0)
             __hip_atomic_store(reinterpret_cast<unsigned long long*>(host_out), (unsigned long long)__double_as_longlong(token), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
     }
 }
 
@@ -431,5 +432,6 @@ int kk_launch_lanczos_fstep(kk_ctx ctx, const kk_sparse_dev& M, double* V, int64
 #undef FS_ARGS
     KK_HIP(hipGetLastError());
     ++ctx->fstep_launches;
+    ctx->fstep_last_blocks = G; ctx->fstep_last_np = NP; ctx->fstep_last_threads = tpb;
     return KK_OK;
 }

@@ -627,6 +627,7 @@ KK_API int kk_arnoldi_expand(kk_op op, kk_basis b, int c0, int k, kk_orth_t orth
                         b->spec_dot_mode == 0 && b->la_kind == 0 && b->la_k == k && b->la_nsweeps == la_sweeps && b->spec_beta == beta_old && strict_route && v_ready;
     const int la_slot = b->la_slot;
     const double la_token = b->la_token;
+    const bool inside_lost = la_hit && b->la_inside;   // the launch enqueued ahead was to form w = A v itself (taken now: la_enqueue below overwrites the flag)
     // the whole step in one launch (short vectors and short bases: kk_kernels_fstep.hip; round 6)
     const bool fs_route = m <= KK_MAX_M && fstep_ok_arnoldi(c, op, b, c0, k, orth, la_sweeps > 0 && kk_mgs_lowsync(c, b->ld, m));
     const bool la_fs_hit = b->la_valid && b->spec_valid && c->spec_owner == b && b->spec_gen == c->foreign_gen && b->spec_op == op && b->spec_c0 == c0 && b->spec_k == k &&
@@ -698,7 +699,7 @@ KK_API int kk_arnoldi_expand(kk_op op, kk_basis b, int c0, int k, kk_orth_t orth
         b->spec_valid = false; b->la_valid = false;
         KK_TRY(stream_sync(c));
         c->persist_norm_done = false;
-        if (b->la_inside) {   // ... unless the lost launch was to form A v itself (k_mgs_panel<.., APPLY>): then nothing has written w yet
+        if (inside_lost) {   // ... unless the lost launch was to form A v itself (k_mgs_panel<.., APPLY>): then nothing has written w yet
             kk_spmv_fuse f;
             KK_TRY(kk_launch_spmv(c, op->A, v, w, b->ld, f));
         }

@@ -27,7 +27,8 @@ def run(kk, c, A, x0, dev, steps, fused, lookahead=1, sym=True):
 @pytest.mark.parametrize("shape", [(36, 30), (131, 77), (512, 200), (498, 500)])
 @pytest.mark.parametrize("orth", ["mgs2", "cgs2"])
 def test_one_launch_step_against_oracle_and_projection_pair(kk, ko, shape, orth):
-    """1 080 .. 250 000 rows (1, 2, 4 and 8 row pairs per thread), odd and even row counts: alpha / beta within 1e-10 of the oracle and 1e-12 of the
+    """1 080 .. 250 000 rows (1, 2 and 4 row pairs per thread at the default 128 blocks; 8 pairs and the 512- / 1024-thread blocks:
+    tests/test_gpu_fstep_envelope.py), odd and even row counts: alpha / beta within 1e-10 of the oracle and 1e-12 of the
     projection pair, V orthonormal, one launch per step (+ the one enqueued ahead), lookahead on and off bit-identical (same kernel either way)"""
     nx, ny = shape
     n = nx * ny

@@ -250,3 +250,36 @@ def test_lost_launch_that_was_to_apply_the_stencil_itself_is_repeated_with_its_a
         assert np.max(np.abs(V.T @ V - np.eye(V.shape[1]))) < 1e-12
     finally:
         c.close()
+
+
+@pytest.mark.parametrize("apply_before,apply_after", [(1, 0), (0, 1)])
+def test_lost_launch_recovery_across_a_change_of_panel_apply(kk, ko, apply_before, apply_after):
+    """the run-ahead launch enqueued with (without) the apply inside gives up (test hook), and "panel_apply" is switched off (on) before the
+    next expand!: the recovery must go by what the LOST launch was to do -- form w = A v itself or not --, not by the launch the same call
+    enqueues behind it (kk_arnoldi_expand takes the flag before la_enqueue overwrites it)"""
+    nx, ny = 600, 500
+    A = ko.convection_diffusion_2d(nx, ny)
+    x0 = np.random.default_rng(8).random(nx * ny)
+    c = kk.Context(0)
+    try:
+        if c.get_option("mgs_persist") == 0:
+            pytest.skip("persistent routes off on this device")
+        c.set_option("panel_min_rows", 0); c.set_option("fused_step", 0); c.set_option("persist_timeout_ms", 20)
+        c.set_option("panel_apply", apply_before)
+        it = kk.ArnoldiIterator(kk.SparseOperator(A, c), x0, kk.ModifiedGramSchmidt2(), capacity=16)
+        f = kk.initialize(it)
+        oit = ko.ArnoldiIterator(A, x0.copy(), ko.MGS2); of = ko.arnoldi_initialize(oit)
+        for i in range(12):
+            if i == 6:
+                a0 = c.get_option("panel_apply_launches")
+                c.set_option("persist_fault", 1)     # the launch enqueued ahead during this call gives up
+            if i == 7:
+                assert (c.get_option("panel_apply_launches") > a0) == bool(apply_before)   # (the lost launch carried the apply, or not)
+                c.set_option("panel_apply", apply_after)
+            f = kk.expand_(it, f); of = ko.arnoldi_expand(oit, of)
+        assert c.get_option("persist_timeouts") == 1
+        assert np.max(np.abs(np.asarray(f.H) - np.asarray(of.H))) < 1e-10 * np.max(np.abs(of.H))
+        V = f.V.to_numpy()
+        assert np.max(np.abs(V.T @ V - np.eye(V.shape[1]))) < 1e-12
+    finally:
+        c.close()
