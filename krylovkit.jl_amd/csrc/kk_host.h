@@ -39,11 +39,15 @@ static const double KK_EPS = std::numeric_limits<double>::epsilon();
 int ws_fetch_async(kk_ctx c, int64_t off, int64_t count, int slot);
 int stream_sync(kk_ctx c);
 static inline const double* pin(kk_ctx c, int64_t off, int slot = 0) { return c->h_pin + (int64_t)slot * WS_TOTAL + off; }
-// any mutation of a slab column: invalidates the cached Gram rows from that column on and a speculative next-step SpMV
+// drops the work enqueued ahead for the basis (kk_ahead): the next expand! runs its step from the slab
+static inline void ahead_void(kk_basis b) {
+    b->ahead.valid = false;
+    b->ahead.kind = kk_ahead_kind::none;
+}
+// any mutation of a slab column: invalidates the cached Gram rows from that column on and the work enqueued ahead
 static inline void gram_touch(kk_basis b, int col) {
     if (col < b->gram_rows) b->gram_rows = col;
-    b->spec_valid = false;
-    b->la_valid = false;
+    ahead_void(b);
     kk_ctx c = b->ctx;   // cached Gram matrix of a residual block: gone as soon as a column at or below its end may have changed
     if (c->gw_valid && c->gw_basis == b->uid && col < c->gw_col + c->gw_p) c->gw_valid = false;
 }

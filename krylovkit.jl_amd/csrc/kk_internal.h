@@ -263,7 +263,7 @@ struct kk_ctx_s {
     bool persist_pending = false;  // a persistent launch has not been checked for a barrier timeout yet
     int persist_slot = 0;          // pinned slot its scalars (and completion token) were fetched into
     double persist_token = 0;      // token COUNTER: the last launch enqueued (a launch that committed wrote its token to SC_PERSIST_OK)
-    double persist_check_token = 0;  // token of the launch `persist_pending` refers to (a run-ahead launch behind it has its own: la_token)
+    double persist_check_token = 0;  // token of the launch `persist_pending` refers to (a run-ahead launch behind it has its own: kk_ahead::token)
     unsigned persist_epoch = 0;    // epochs handed out so far: tags of the grid reductions are unique over the life of the context
     bool persist_norm_req = false; // the caller of the sweep wants w / |w| stored (expand!'s scale of the next step, orthonormalize!!)
     bool persist_norm_done = false;  // ... and the last sweep went through a launch that was asked to do so
@@ -309,6 +309,27 @@ struct kk_ctx_s {
     std::vector<hipEvent_t> event_pool;
 };
 
+// Work one expand! enqueued for the NEXT call of its factorization (hides the host round trip between two calls): the apply of the next
+// step and, on some routes, the whole step behind it.  Written by ahead_arm_apply / ahead_arm_step (kk_krylov.hip), dropped by ahead_void
+// (kk_host.h); the step part exists only behind a valid apply.
+enum class kk_ahead_kind { none, sweep /* persistent MGS sweep(s) */, projection /* projection-based Lanczos step */, one_launch /* k_lanczos_fstep */ };
+enum class kk_solver { lanczos, arnoldi };
+struct kk_ahead {
+    bool valid = false;                // the apply: taken over if (owner, gen, op, c0, k, beta) and the route's own terms match
+    uint64_t gen = 0;                  // ctx->foreign_gen when it (and what was enqueued behind it) went out
+    const void* op = nullptr;
+    int c0 = 0, k = 0, dot_mode = 0;   // dot_mode -1: the one-launch step (no separate apply)
+    const double* dot_ptr = nullptr;   // device slot that received the apply's inner product
+    double beta = 0;
+    kk_ahead_kind kind = kk_ahead_kind::none;   // the step behind it, for basis size k + 1
+    kk_solver solver = kk_solver::lanczos;
+    kk_orth_t orth = KK_CGS;
+    int slot = 0, nsweeps = 0;         // pinned slot of its read-back; persistent sweeps in its launch
+    double token = 0;                  // completion token of its launch (sweep, one_launch)
+    bool rode = false;                 // projection: the new Gram row came with the read-back
+    bool inside = false;               // sweep: the launch formed A v itself (<.., APPLY>): if it is lost, the apply has to be repeated too
+};
+
 struct kk_basis_s {
     kk_ctx ctx = nullptr;
     uint64_t uid = 0;   // unique over the life of the process (a freed slab's address may be reused)
@@ -323,21 +344,7 @@ struct kk_basis_s {
     int gram_rows = 0;  // rows [0, gram_rows) of the strictly-lower Gram matrix are valid
     double* d_gram = nullptr;  // device mirror of `gram` (same layout), valid for the same rows
     double* d_gdiag = nullptr; // device only: |b_i|^2 - 1 where a block step measured it (0 elsewhere), rows as d_gram
-    // speculative next-step SpMV (hides the host round trip between two expand! calls)
-    bool spec_valid = false;
-    uint64_t spec_gen = 0;       // ctx->foreign_gen when the speculative apply (and what was enqueued behind it) went out
-    const void* spec_op = nullptr;
-    int spec_c0 = 0, spec_k = 0, spec_dot_mode = 0;
-    const double* spec_dot_ptr = nullptr;   // device slot that received the speculative apply's inner product
-    double spec_beta = 0;
-    // the whole next step (apply + persistent sweep + read-back) enqueued one call ahead: valid only together with spec_valid
-    bool la_valid = false;
-    int la_k = 0, la_slot = 0, la_nsweeps = 0;
-    double la_token = 0;
-    int la_kind = 0;          // 0: persistent sweep (la_token), 1: projection-based Lanczos step (CGS2 / low-sync MGS2: la_orth, la_rode), 2: one-launch step (k_lanczos_fstep: la_token = its token)
-    int la_orth = 0;
-    bool la_rode = false;
-    bool la_inside = false;   // the launch enqueued ahead formed A v itself (k_mgs_panel<.., APPLY>): if it is lost, the apply has to be repeated too
+    kk_ahead ahead;   // work enqueued one call ahead for the next expand! of this factorization (kk_krylov.hip)
     // residual column left NORMALISED by a fused expand! (persistent kernel, w / |w| written at commit): logically the column
     // still holds r = norm_beta * stored; the next expand! of the same factorization takes it as its new basis vector without
     // the scale pass, every other access multiplies it back first (norm_flush)

@@ -87,6 +87,28 @@ KK_API int kk_arnoldi_initialize(kk_op op, kk_basis b, int c0, kk_orth_t orth, d
     return krylov_initialize(op, b, c0, orth, eta, alpha, beta);
 }
 
+// ---- work enqueued one call ahead (kk_ahead, kk_internal.h) --------------------------------------------------------------------------
+// The key every consumer checks: the record was written for this basis in the context's current generation (no entry point handed
+// another slab launched anything since: ctx_foreign_touch), for exactly this step.  Each route adds its own terms.
+static bool ahead_matches(kk_basis b, kk_op op, int c0, int k, double beta_old) {
+    const kk_ahead& a = b->ahead;
+    kk_ctx c = b->ctx;
+    return a.valid && c->spec_owner == b && a.gen == c->foreign_gen && a.op == op && a.c0 == c0 && a.k == k && a.beta == beta_old;
+}
+static void ahead_arm_apply(kk_basis b, kk_op op, int c0, int k, int dot_mode, const double* dot_ptr, double beta) {
+    kk_ahead a;
+    a.valid = true; a.gen = b->ctx->foreign_gen; a.op = op; a.c0 = c0; a.k = k; a.dot_mode = dot_mode; a.dot_ptr = dot_ptr; a.beta = beta;
+    b->ahead = a;
+    b->ctx->spec_owner = b;
+}
+// ... and the whole step behind the apply armed last (a step without its apply is not recorded)
+static void ahead_arm_step(kk_basis b, kk_ahead_kind kind, kk_solver solver, kk_orth_t orth, int slot, double token, int nsweeps = 0,
+                           bool rode = false, bool inside = false) {
+    kk_ahead& a = b->ahead;
+    if (!a.valid) return;
+    a.kind = kind; a.solver = solver; a.orth = orth; a.slot = slot; a.token = token; a.nsweeps = nsweeps; a.rode = rode; a.inside = inside;
+}
+
 // Speculative first half of the NEXT expand!: w' = A (r/beta) - beta v  with the scale applied on
 // the fly from the device-resident beta, so the GPU keeps working while the host reads back
 // (alpha, beta), returns to the caller and re-enters.  r itself is NOT modified; the next expand
@@ -95,22 +117,8 @@ KK_API int kk_arnoldi_initialize(kk_op op, kk_basis b, int c0, kk_orth_t orth, d
 static int speculate_next(kk_op op, kk_basis b, int c0, int k_next, int dot_mode, bool with_prev, double beta_host, double* dot_out = nullptr,
                           bool inside_sweep = false /* the sweep launch that follows forms A v itself (c->sweep_apply): nothing is launched here */) {
     kk_ctx c = b->ctx;
-    b->spec_valid = false;
+    ahead_void(b);
     if (!c->speculate || c0 + k_next + 2 > b->cap || k_next + 1 > KK_MAX_M) return KK_OK;
-    if (inside_sweep) {
-        kk_spmv_fuse fi;
-        fi.xscale_dev = c->persist_norm_done ? SCP(c, SC_XS) : SCP(c, SC_INVNRM);
-        if (with_prev) { fi.vprev = b->col(c0 + k_next - 1); fi.bprev_dev = SCP(c, SC_NRM); }
-        fi.dot_mode = dot_mode;
-        fi.dot_out = dot_out ? dot_out : SCP(c, SC_SPECA);
-        c->sweep_apply.on = true; c->sweep_apply.M = &op->A; c->sweep_apply.x = b->col(c0 + k_next); c->sweep_apply.f = fi;
-        b->spec_dot_ptr = fi.dot_mode ? fi.dot_out : nullptr;
-        b->spec_valid = true; b->spec_op = op; b->spec_c0 = c0; b->spec_k = k_next; b->spec_dot_mode = dot_mode;
-        b->spec_beta = beta_host;
-        c->spec_owner = b;
-        b->spec_gen = c->foreign_gen;
-        return KK_OK;
-    }
     kk_spmv_fuse f;
     // a sweep that went through a normalising persistent launch left r / |r| in the column (or r itself when the norm was
     // zero): the kernel wrote the factor that is still to be applied -- 1 or 1/|r| -- to SC_XS
@@ -120,28 +128,24 @@ static int speculate_next(kk_op op, kk_basis b, int c0, int k_next, int dot_mode
     // (where the speculative <v, w> lands: its own slot, or -- when the caller knows that every read-back of the current step
     // is in the stream already -- directly the slot the next call's sweep reads: no device-to-device copy at the next call)
     f.dot_out = dot_out ? dot_out : SCP(c, SC_SPECA);
-    KK_TRY(kk_launch_spmv(c, op->A, b->col(c0 + k_next), b->col(c0 + k_next + 1), b->ld, f));
-    b->spec_dot_ptr = f.dot_out;
-    b->spec_valid = true; b->spec_op = op; b->spec_c0 = c0; b->spec_k = k_next; b->spec_dot_mode = dot_mode;
-    b->spec_beta = beta_host;
-    c->spec_owner = b;
-    b->spec_gen = c->foreign_gen;
+    if (inside_sweep) {
+        c->sweep_apply.on = true; c->sweep_apply.M = &op->A; c->sweep_apply.x = b->col(c0 + k_next); c->sweep_apply.f = f;
+    } else {
+        KK_TRY(kk_launch_spmv(c, op->A, b->col(c0 + k_next), b->col(c0 + k_next + 1), b->ld, f));
+    }
+    ahead_arm_apply(b, op, c0, k_next, dot_mode, f.dot_out, beta_host);
     return KK_OK;
 }
-// true if the previous expand on this basis already enqueued exactly this step's SpMV; moves the
-// speculative alpha into the regular slot
+// true if the previous expand on this basis already enqueued exactly this step's SpMV and nothing behind it (a step enqueued
+// ahead that this call does not take has consumed the apply's output column); moves the speculative alpha into the regular slot
 static int spec_take(kk_op op, kk_basis b, int c0, int k, int dot_mode, double beta_old, double* a0_slot, bool* hit) {
-    kk_ctx c = b->ctx;
-    *hit = b->spec_valid && c->spec_owner == b && b->spec_gen == c->foreign_gen && b->spec_op == op && b->spec_c0 == c0 && b->spec_k == k &&
-           b->spec_dot_mode == dot_mode && b->spec_beta == beta_old;
-    if (*hit && dot_mode && b->spec_dot_ptr != a0_slot)
-        KK_HIP(hipMemcpyAsync(a0_slot, b->spec_dot_ptr, sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    const kk_ahead& a = b->ahead;
+    *hit = ahead_matches(b, op, c0, k, beta_old) && a.dot_mode == dot_mode && a.kind == kk_ahead_kind::none;
+    if (*hit && dot_mode && a.dot_ptr != a0_slot)
+        KK_HIP(hipMemcpyAsync(a0_slot, a.dot_ptr, sizeof(double), hipMemcpyDeviceToDevice, b->ctx->stream));
     return KK_OK;
 }
-// the last synchronisation of an expand: a pending speculation request (Arnoldi) is enqueued first
-// The host waits only for the read-backs queued so far (event), NOT for the speculative SpMV that
-// is enqueued behind them -- that one keeps the GPU busy during the host round trip.
-static int la_enqueue(kk_op op, kk_basis b, int c0, int j, int nsweeps, bool lanczos_carry);
+static int la_enqueue(kk_op op, kk_basis b, int c0, int j, int nsweeps, kk_solver s);
 // the run-ahead of an Arnoldi step (la_enqueue below) will go through the panel kernel, which can apply this operator itself: same conditions as
 // la_enqueue's own + kk_sweep_apply_ok
 static bool la_apply_inside(kk_op op, kk_basis b, int c0, int j, int nsweeps) {
@@ -162,6 +166,22 @@ static bool la_apply_inside_lanczos(kk_op op, kk_basis b, int c0, int j) {
     if (kk_mgs_lowsync(c, b->ld, m)) return false;
     return kk_sweep_apply_ok_persist(c, op->A, b->ld, m);
 }
+// The next step's apply (Lanczos: w = A v - beta v_prev with alpha0 straight to its slot; |w| and 1 / |w| are on the device) and, with
+// `nsweeps` persistent MGS sweeps, the whole next step behind it (la_enqueue).  The apply is handed to that sweep launch where it can
+// form A v itself; if la_enqueue declines after all, the apply goes out as its own launch -- nobody is left to consume the request.
+static int enqueue_next(kk_op op, kk_basis b, int c0, int k_next, int nsweeps, kk_solver s) {
+    kk_ctx c = b->ctx;
+    const bool lz = s == kk_solver::lanczos;
+    double* dot_out = lz ? SCP(c, SC_ALPHA0) : nullptr;
+    const bool inside = nsweeps > 0 && (lz ? la_apply_inside_lanczos(op, b, c0, k_next) : la_apply_inside(op, b, c0, k_next, nsweeps));
+    KK_TRY(speculate_next(op, b, c0, k_next, lz ? 2 : 0, lz, 0.0, dot_out, inside));
+    if (nsweeps > 0) KK_TRY(la_enqueue(op, b, c0, k_next, nsweeps, s));
+    if (c->sweep_apply.on) {   // (la_enqueue declined)
+        c->sweep_apply.on = false;
+        KK_TRY(speculate_next(op, b, c0, k_next, lz ? 2 : 0, lz, 0.0, dot_out));
+    }
+    return KK_OK;
+}
 int fetch_mark(kk_ctx c) {
     KK_HIP(hipEventRecord(c->ev_fetch, c->stream));
     return KK_OK;
@@ -170,21 +190,16 @@ int fetch_wait(kk_ctx c) {
     KK_HIP(hipEventSynchronize(c->ev_fetch));
     return KK_OK;
 }
+// the last synchronisation of an expand: a pending speculation request (Arnoldi) is enqueued first
+// The host waits only for the read-backs queued so far (event), NOT for the speculative SpMV that
+// is enqueued behind them -- that one keeps the GPU busy during the host round trip.
 int final_sync(kk_ctx c) {
-    if (c->spec_req.active) {
-        c->spec_req.active = false;
-        KK_TRY(fetch_mark(c));
-        const bool inside = c->spec_req.la_nsweeps > 0 && la_apply_inside(c->spec_req.op, c->spec_req.b, c->spec_req.c0, c->spec_req.k_next, c->spec_req.la_nsweeps);
-        KK_TRY(speculate_next(c->spec_req.op, c->spec_req.b, c->spec_req.c0, c->spec_req.k_next, 0, false, 0.0, nullptr, inside));
-        if (c->spec_req.la_nsweeps > 0)   // Arnoldi with a persistent MGS / MGS2 sweep: the whole next step behind its apply (see la_enqueue)
-            KK_TRY(la_enqueue(c->spec_req.op, c->spec_req.b, c->spec_req.c0, c->spec_req.k_next, c->spec_req.la_nsweeps, false));
-        if (c->sweep_apply.on) {   // (la_enqueue declined after all: the apply goes out as its own launch -- nobody is left to consume the request)
-            c->sweep_apply.on = false;
-            KK_TRY(speculate_next(c->spec_req.op, c->spec_req.b, c->spec_req.c0, c->spec_req.k_next, 0, false, 0.0));
-        }
-        return fetch_wait(c);
-    }
-    return stream_sync(c);
+    if (!c->spec_req.active) return stream_sync(c);
+    c->spec_req.active = false;
+    KK_TRY(fetch_mark(c));
+    const auto r = c->spec_req;   // (with a persistent MGS / MGS2 sweep: the whole next step behind its apply)
+    KK_TRY(enqueue_next(r.op, r.b, r.c0, r.k_next, r.la_nsweeps, kk_solver::arnoldi));
+    return fetch_wait(c);
 }
 
 // Run-ahead of a whole step (Lanczos, MGS2 in the strict / panel order, one GPU): once the speculative apply of step j is in
@@ -195,14 +210,14 @@ int final_sync(kk_ctx c) {
 // Same kernels, same operands, same order as the call-by-call route: bit-identical results.  Not enqueued when the step after
 // it would no longer fit the slab (c0 + j + 3 > capacity): with the usual capacity of krylovdim + 2 the run-ahead stops at the
 // last step of a Krylov cycle instead of wasting a sweep the caller will never ask for.
-static int la_enqueue(kk_op op, kk_basis b, int c0, int j, int nsweeps, bool lanczos_carry) {
+static int la_enqueue(kk_op op, kk_basis b, int c0, int j, int nsweeps, kk_solver s) {
     kk_ctx c = b->ctx;
-    b->la_valid = false;
+    const bool lanczos_carry = s == kk_solver::lanczos;
     const int m = j + 1;
-    if (!c->lookahead || !c->fold_scale || !b->spec_valid || !c->persist_norm_done || (kk_sharded(c) && !kk_xs_on(c)) || c->persist_skip > 0) return KK_OK;
+    if (!c->lookahead || !c->fold_scale || !b->ahead.valid || !c->persist_norm_done || (kk_sharded(c) && !kk_xs_on(c)) || c->persist_skip > 0) return KK_OK;
     if (m > KK_MAX_M || c0 + j + 3 > b->cap) return KK_OK;
     if (!(kk_mgs_panel_eligible(c, b->ld) || kk_mgs_persist_eligible(c, b->ld, m, nsweeps)) || kk_mgs_lowsync(c, b->ld, m)) return KK_OK;
-    if (lanczos_carry && b->spec_dot_ptr != SCP(c, SC_ALPHA0)) return KK_OK;   // (alpha0 of step j must sit where the sweep reads it)
+    if (lanczos_carry && b->ahead.dot_ptr != SCP(c, SC_ALPHA0)) return KK_OK;   // (alpha0 of step j must sit where the sweep reads it)
     const int slot = 2 + (j & 1);
     const int64_t offs[2] = {WS_S, WS_G};
     c->persist_norm_req = true;
@@ -210,7 +225,7 @@ static int la_enqueue(kk_op op, kk_basis b, int c0, int j, int nsweeps, bool lan
     // The CURRENT step's launch may still be waiting for its check (persist_pending, slot 0, its token): the nested sweep below
     // must not take its place -- the caller's persist_check has to look at THAT launch (with the bookkeeping
     // overwritten here a barrier timeout of the first launch of a run-ahead chain went unnoticed).  The launch enqueued ahead
-    // is identified by (la_slot, la_token) and checked by the next call.
+    // is identified by (ahead.slot, ahead.token) and checked by the next call.
     const bool cur_pending = c->persist_pending;
     const int cur_slot = c->persist_slot;
     const double cur_token = c->persist_check_token;
@@ -225,8 +240,7 @@ static int la_enqueue(kk_op op, kk_basis b, int c0, int j, int nsweeps, bool lan
     KK_TRY(st);
     if (!ahead_persistent) return KK_OK;   // (took the launch-per-vector route: results are simply not used ahead)
     KK_HIP(hipEventRecord(c->ev_la[slot & 1], c->stream));
-    b->la_valid = true; b->la_k = j; b->la_slot = slot; b->la_token = ahead_token; b->la_nsweeps = nsweeps; b->la_kind = 0;
-    b->la_inside = c->sweep_apply_fused;
+    ahead_arm_step(b, kk_ahead_kind::sweep, s, lanczos_carry || nsweeps > 1 ? KK_MGS2 : KK_MGS, slot, ahead_token, nsweeps, false, c->sweep_apply_fused);
     return KK_OK;
 }
 
@@ -267,10 +281,9 @@ static int lanczos_proj_enqueue(kk_basis b, int c0, int k, kk_orth_t orth, int s
 // other access settles it exactly as after a persistent sweep.
 static int la_enqueue_proj(kk_op op, kk_basis b, int c0, int j, kk_orth_t orth) {
     kk_ctx c = b->ctx;
-    b->la_valid = false;
     const int m = j + 1;
-    if (!c->lookahead || !c->fold_scale || !b->spec_valid || kk_sharded(c)) return KK_OK;
-    if (m > KK_MAX_M || c0 + j + 3 > b->cap || b->spec_dot_ptr != SCP(c, SC_ALPHA0)) return KK_OK;
+    if (!c->lookahead || !c->fold_scale || !b->ahead.valid || kk_sharded(c)) return KK_OK;
+    if (m > KK_MAX_M || c0 + j + 3 > b->cap || b->ahead.dot_ptr != SCP(c, SC_ALPHA0)) return KK_OK;
     if (orth == KK_MGS2 && c0 != 0) return KK_OK;
     const int slot = 2 + (j & 1);
     // v_j = r / beta in place, beta still on the device only
@@ -278,23 +291,16 @@ static int la_enqueue_proj(kk_op op, kk_basis b, int c0, int j, kk_orth_t orth) 
     bool rode = false;
     KK_TRY(lanczos_proj_enqueue(b, c0, j, orth, slot, orth == KK_MGS2 ? j : 0, &rode));   // (Gram row j - 1 is being produced by the step in front)
     KK_HIP(hipEventRecord(c->ev_la[slot & 1], c->stream));
-    b->la_valid = true; b->la_k = j; b->la_slot = slot; b->la_nsweeps = 0; b->la_kind = 1; b->la_orth = (int)orth; b->la_rode = rode;
+    ahead_arm_step(b, kk_ahead_kind::projection, kk_solver::lanczos, orth, slot, 0.0, 0, rode);
     return KK_OK;
 }
 
 // ---- the whole step in one launch (short vectors: kk_kernels_fstep.hip).  Single-rank context, operator in the ELL format without
 // ghost columns, factorization starting at column 0, at most KK_FS_MAX_M basis vectors, CGS2 or MGS2 in its low-synchronisation form.
-static bool fstep_ok_common(kk_ctx c, kk_op op, kk_basis b, int c0, int k);
-static bool fstep_ok(kk_ctx c, kk_op op, kk_basis b, int c0, int k, kk_orth_t orth, bool lowsync) {
-    if (!(orth == KK_CGS2 || (orth == KK_MGS2 && lowsync))) return false;
-    return fstep_ok_common(c, op, b, c0, k);
-}
 // Arnoldi: the same launch without the three-term part, one (CGS, MGS) or two (CGS2, MGS2) orthogonalisation passes; MGS family in its low-sync form
-static bool fstep_ok_arnoldi(kk_ctx c, kk_op op, kk_basis b, int c0, int k, kk_orth_t orth, bool lowsync) {
-    if (!(orth == KK_CGS || orth == KK_CGS2 || ((orth == KK_MGS || orth == KK_MGS2) && lowsync))) return false;
-    return fstep_ok_common(c, op, b, c0, k);
-}
-static bool fstep_ok_common(kk_ctx c, kk_op op, kk_basis b, int c0, int k) {
+static bool fstep_ok(kk_ctx c, kk_op op, kk_basis b, int c0, int k, kk_orth_t orth, bool lowsync, kk_solver s) {
+    const bool arnoldi = s == kk_solver::arnoldi;
+    if (!(orth == KK_CGS2 || (arnoldi && orth == KK_CGS) || ((orth == KK_MGS2 || (arnoldi && orth == KK_MGS)) && lowsync))) return false;
     if (!c->fused_step || !c->d_fsync || kk_sharded(c) || c->allreduce || (c->comm && c->comm->active)) return false;
     if (c0 != 0 || k < 1 || k + 1 > KK_FS_MAX_M) return false;
     // The one launch wins while the basis is SHORT as well: its fixed cost is ~8-15 us against ~28 us of the projection pair's ten stream
@@ -314,9 +320,10 @@ static inline double* fstep_slot(kk_ctx c, int slot) { return c->h_pin + (int64_
 // enqueue the step for basis size m = k + 1 (v = column k, normalised IN THE STREAM); the kernel reads beta of the step in front from
 // the device (bprev_dev) or takes the host's value
 static int fstep_enqueue(kk_op op, kk_basis b, int k, kk_orth_t orth, const double* bprev_dev, double bprev, int rows_in_stream, int slot, double* token_out,
-                         bool arnoldi = false) {
+                         kk_solver s) {
     kk_ctx c = b->ctx;
     const int m = k + 1;
+    const bool arnoldi = s == kk_solver::arnoldi;
     const bool ls = orth == KK_MGS2 || orth == KK_MGS;
     const int npass = arnoldi && (orth == KK_CGS2 || orth == KK_MGS2) ? 2 : 1;
     if (ls) {   // Gram rows of the basis columns below the newest one (lowsync_project_dev): known, on their way in the stream, or recomputed (restart)
@@ -341,6 +348,43 @@ static bool fstep_wait(kk_ctx c, int slot, double token) {
     (void)hipStreamSynchronize(c->stream);   // (a launch that is merely late has arrived now; one that gave up never will)
     std::atomic_thread_fence(std::memory_order_acquire);
     return h[0] == token;
+}
+// The step through the one launch, both solvers: the launch the previous call enqueued for it (`taken`) or a new one; the NEXT step's
+// launch goes out before the host looks at this one's token (Lanczos: it reads beta of this step from the device).  *hs: the pinned
+// slot with the step's results, its Gram row committed and its normalised column noted.  *hs == nullptr: the launch gave up (a block
+// that never became resident: GPU shared with another job).  Column k holds v = r / beta_old, nothing else of the factorization was
+// touched: the route is switched off for this context and the caller runs the step again on the ordinary one.
+static int fstep_run(kk_op op, kk_basis b, int c0, int k, kk_orth_t orth, kk_solver s, double beta_old, bool lowsync_next, const kk_ahead* taken,
+                     const double** hs) {
+    kk_ctx c = b->ctx;
+    const bool lanczos = s == kk_solver::lanczos;
+    *hs = nullptr;
+    int slot = 2 + (k & 1);
+    double token = 0;
+    if (taken) { slot = taken->slot; token = taken->token; }
+    else KK_TRY(fstep_enqueue(op, b, k, orth, nullptr, lanczos ? beta_old : 0.0, 0, slot, &token, s));
+    ahead_void(b);
+    if (c->lookahead && c->fold_scale && c0 + k + 3 <= b->cap && fstep_ok(c, op, b, c0, k + 1, orth, lowsync_next, s)) {
+        const int next = 2 + ((k + 1) & 1);
+        double tk = 0;
+        KK_TRY(fstep_enqueue(op, b, k + 1, orth, lanczos ? SCP(c, SC_NRM) : nullptr, 0.0, k + 1, next, &tk, s));
+        ahead_arm_apply(b, op, c0, k + 1, -1, nullptr, 0.0);
+        ahead_arm_step(b, kk_ahead_kind::one_launch, s, orth, next, tk);
+    }
+    if (!fstep_wait(c, slot, token)) {
+        KK_HIP(hipMemsetAsync((char*)c->d_fsync + KK_FS_SYNC_BYTES, 0, sizeof(int), c->stream));
+        ++c->fstep_failures;
+        c->fused_step = 0;
+        ahead_void(b);
+        b->norm_col = c0 + k; b->norm_beta = beta_old;   // (v is normalised in place already: the repeated call must not scale it again)
+        return KK_OK;
+    }
+    const double* h = fstep_slot(c, slot);
+    if (orth == KK_MGS || orth == KK_MGS2) lowsync_commit_row(b, k + 1, h + 8);
+    if (h[6] != 0.0 && kk_persist_norm_applies(h[4])) { b->norm_col = c0 + k + 1; b->norm_beta = h[4]; }
+    else ahead_void(b);   // (zero / overflowing norm: the column holds w itself, the step enqueued behind it is void)
+    *hs = h;
+    return KK_OK;
 }
 
 KK_API int kk_lanczos_expand(kk_op op, kk_basis b, int c0, int k, kk_orth_t orth, double eta, double beta_old,
@@ -376,17 +420,12 @@ KK_API int kk_lanczos_expand(kk_op op, kk_basis b, int c0, int k, kk_orth_t orth
     // the previous call may have enqueued this WHOLE step already (apply, sweep and read-back: la_enqueue below)
     const bool strict_branch = orth == KK_MGS2 && !wide && !sh_fused && !(lowsync && c0 == 0);
     const bool proj_branch = !wide && !sh_fused && (orth == KK_CGS2 || (orth == KK_MGS2 && lowsync && c0 == 0));
-    const bool la_same = b->la_valid && b->spec_valid && c->spec_owner == b && b->spec_gen == c->foreign_gen && b->spec_op == op && b->spec_c0 == c0 && b->spec_k == k &&
-                         b->la_k == k && b->spec_beta == beta_old && v_ready;
-    const bool fs_route = proj_branch && fstep_ok(c, op, b, c0, k, orth, lowsync);   // the whole step in one launch (short vectors)
-    const bool la_hit = la_same && b->la_kind == 0 && b->la_nsweeps == 1 && strict_branch;
-    const bool la_proj_hit = la_same && b->la_kind == 1 && b->la_orth == (int)orth && proj_branch && !kk_sharded(c) && !fs_route;
-    const bool la_fs_hit = la_same && b->la_kind == 2 && b->la_orth == (int)orth && fs_route;
-    const int la_slot = b->la_slot;
-    const double la_token = b->la_token;
-    if (b->la_valid && !la_hit && !la_proj_hit && !la_fs_hit) b->spec_valid = false;   // a sweep enqueued ahead has consumed the speculative apply's output column: nothing to take over
-    const int la_proj_slot = b->la_slot;
-    const bool la_proj_rode = b->la_rode;
+    const kk_ahead taken = b->ahead;   // (what this call consumes: the record itself is overwritten by the step it enqueues ahead)
+    const bool la_same = ahead_matches(b, op, c0, k, beta_old) && v_ready;
+    const bool fs_route = proj_branch && fstep_ok(c, op, b, c0, k, orth, lowsync, kk_solver::lanczos);   // the whole step in one launch (short vectors)
+    const bool la_hit = la_same && taken.kind == kk_ahead_kind::sweep && taken.nsweeps == 1 && strict_branch;
+    const bool la_proj_hit = la_same && taken.kind == kk_ahead_kind::projection && taken.orth == orth && proj_branch && !kk_sharded(c) && !fs_route;
+    const bool la_fs_hit = la_same && taken.kind == kk_ahead_kind::one_launch && taken.solver == kk_solver::lanczos && taken.orth == orth && fs_route;
     bool hit = la_hit || la_proj_hit || la_fs_hit;
     if (!hit && !fs_route) KK_TRY(spec_take(op, b, c0, k, cgs_order ? 1 : 2, beta_old, a0_slot, &hit));
     gram_touch(b, c0 + k);
@@ -474,37 +513,13 @@ KK_API int kk_lanczos_expand(kk_op op, kk_basis b, int c0, int k, kk_orth_t orth
         passes = 1;
     } else if (fs_route) {
         // ONE launch per step (k_lanczos_fstep): apply, both grid reductions, the small solve, the update and the normalised commit; the scalars
-        // arrive in a pinned slot the host polls.  The NEXT step's launch goes out before the host looks at this one's token.
-        const int m1 = k + 1;
-        int slot = 2 + (k & 1);
-        double token = 0;
-        if (la_fs_hit) { slot = la_slot; token = la_token; }
-        else KK_TRY(fstep_enqueue(op, b, k, orth, nullptr, beta_old, 0, slot, &token));
-        b->spec_valid = false; b->la_valid = false;
-        if (c->lookahead && c->fold_scale && c0 + k + 3 <= b->cap && fstep_ok(c, op, b, c0, k + 1, orth, lowsync)) {
-            double tk = 0;
-            KK_TRY(fstep_enqueue(op, b, k + 1, orth, SCP(c, SC_NRM), 0.0, m1, 2 + ((k + 1) & 1), &tk));   // (beta of THIS step: on the device when that launch starts)
-            b->spec_valid = true; b->spec_op = op; b->spec_c0 = c0; b->spec_k = k + 1; b->spec_dot_mode = -1; b->spec_beta = 0.0; b->spec_dot_ptr = nullptr;
-            c->spec_owner = b; b->spec_gen = c->foreign_gen;
-            b->la_valid = true; b->la_k = k + 1; b->la_slot = 2 + ((k + 1) & 1); b->la_token = tk; b->la_nsweeps = 0; b->la_kind = 2; b->la_orth = (int)orth; b->la_rode = false;
-        }
-        if (!fstep_wait(c, slot, token)) {
-            // the launch gave up (a block that never became resident: GPU shared with another job).  Column k holds v = r / beta_old, nothing else of
-            // the factorization was touched: the route is switched off for this context and the step runs again on the ordinary one
-            KK_HIP(hipMemsetAsync((char*)c->d_fsync + KK_FS_SYNC_BYTES, 0, sizeof(int), c->stream));
-            ++c->fstep_failures;
-            c->fused_step = 0;
-            b->spec_valid = false; b->la_valid = false;
-            b->norm_col = c0 + k; b->norm_beta = beta_old;   // (v is normalised in place already: the repeated call must not scale it again)
-            return kk_lanczos_expand(op, b, c0, k, orth, eta, beta_old, alpha, beta, npasses);
-        }
-        const double* h = fstep_slot(c, slot);
+        // arrive in a pinned slot the host polls
+        const double* h = nullptr;
+        KK_TRY(fstep_run(op, b, c0, k, orth, kk_solver::lanczos, beta_old, lowsync, la_fs_hit ? &taken : nullptr, &h));
+        if (!h) return kk_lanczos_expand(op, b, c0, k, orth, eta, beta_old, alpha, beta, npasses);
         a = h[1] + h[2];
         bt = h[4];
-        if (orth == KK_MGS2) lowsync_commit_row(b, m1, h + 8);
         passes = 1;
-        if (h[6] != 0.0 && kk_persist_norm_applies(bt)) { b->norm_col = c0 + k + 1; b->norm_beta = bt; }
-        else { b->la_valid = false; b->spec_valid = false; }   // (zero / overflowing norm: the column holds w itself, the step enqueued behind it is void)
     } else if (orth == KK_CGS2 || (orth == KK_MGS2 && lowsync && c0 == 0)) {
         // projection-based step (lanczos_proj_enqueue): s = V'(w - alpha0 v) [exact triangular solve for MGS2], w <- w - V (s + alpha0 e_m),
         // beta = |w|; one host synchronisation.  With the run-ahead (la_enqueue_proj) this call finds its step in the stream already.
@@ -512,8 +527,8 @@ KK_API int kk_lanczos_expand(kk_op op, kk_basis b, int c0, int k, kk_orth_t orth
         int slot = 0;
         bool rode = false;
         if (la_proj_hit) {
-            slot = la_proj_slot;
-            rode = la_proj_rode;
+            slot = taken.slot;
+            rode = taken.rode;
         } else {
             KK_TRY(lanczos_proj_enqueue(b, c0, k, orth, 0, 0, &rode));
             KK_TRY(fetch_mark(c));
@@ -530,15 +545,15 @@ KK_API int kk_lanczos_expand(kk_op op, kk_basis b, int c0, int k, kk_orth_t orth
         bt = pin(c, WS_SCAL + SC_NRM, slot)[0];
         passes = 1;
         // the step enqueued ahead has scaled the new residual column in place: logically it still holds r = bt * column
-        if (b->la_valid && b->la_kind == 1) {
+        if (b->ahead.kind == kk_ahead_kind::projection) {
             if (kk_persist_norm_applies(bt)) { b->norm_col = c0 + k + 1; b->norm_beta = bt; }
-            else { b->la_valid = false; b->spec_valid = false; }   // (zero / overflowing norm: the kernel left the column alone; the step behind it is void)
+            else ahead_void(b);   // (zero / overflowing norm: the kernel left the column alone; the step behind it is void)
         }
     } else if (orth == KK_MGS2) {
         // strict: w -= alpha0 v fused with the first dot of the sweep   lanczos.jl:329-334
         const int64_t offs[1] = {WS_S};
         int slot = 0;
-        bool inside_lost = la_hit && b->la_inside;   // the launch in question (this call's, or the one enqueued ahead) formed w and alpha0 itself
+        bool inside_lost = la_hit && taken.inside;   // the launch in question (this call's, or the one enqueued ahead) formed w and alpha0 itself
         for (int attempt = 0;; ++attempt) {
             const bool ahead = la_hit && attempt == 0;   // this step's sweep and read-back are in the stream already
             if (!ahead) {
@@ -551,29 +566,21 @@ KK_API int kk_lanczos_expand(kk_op op, kk_basis b, int c0, int k, kk_orth_t orth
                 KK_TRY(fetch_mark(c));
                 slot = 0;
             } else {
-                slot = la_slot;
+                slot = taken.slot;
             }
-            if (attempt == 0 && (!kk_sharded(c) || kk_xs_on(c))) {   // (row-sharded: only when the sweep reduces over the ranks inside its launch)
-                const bool inside = la_apply_inside_lanczos(op, b, c0, k + 1);
-                KK_TRY(speculate_next(op, b, c0, k + 1, 2, true, 0.0, SCP(c, SC_ALPHA0), inside));   // |w| and 1/|w| are on the device; alpha0 straight to its slot
-                KK_TRY(la_enqueue(op, b, c0, k + 1, 1, true));                                   // ... and, where it pays, the whole next step behind it
-                if (c->sweep_apply.on) {   // (la_enqueue declined after all: the apply as its own launch)
-                    c->sweep_apply.on = false;
-                    KK_TRY(speculate_next(op, b, c0, k + 1, 2, true, 0.0, SCP(c, SC_ALPHA0)));
-                }
-            }
+            if (attempt == 0 && (!kk_sharded(c) || kk_xs_on(c)))   // (row-sharded: only when the sweep reduces over the ranks inside its launch)
+                KK_TRY(enqueue_next(op, b, c0, k + 1, 1, kk_solver::lanczos));
             if (ahead) KK_HIP(hipEventSynchronize(c->ev_la[slot & 1]));
             else KK_TRY(fetch_wait(c));
             bool redo = false;
-            if (ahead) KK_TRY(persist_check_at(c, slot, la_token, &redo));
+            if (ahead) KK_TRY(persist_check_at(c, slot, taken.token, &redo));
             else KK_TRY(persist_check(c, &redo));
             if (!redo) break;
             // The grid barrier of the persistent kernel timed out (GPU shared with another job): no block wrote w back, so w
             // = A v - beta_old v_prev, the pending pair (v, alpha0) and the basis are exactly what the sweep started from.  v has
             // already been scaled and the SpMV is done -- neither is repeated; only the sweep runs again, on the
             // launch-per-vector route, and everything enqueued ahead (which consumed the norm of the failed launch) is dropped.
-            b->spec_valid = false;
-            b->la_valid = false;
+            ahead_void(b);
             KK_CHECK(attempt == 0, KK_ERR_HIP, "kk_lanczos_expand: the launch-per-vector MGS route reported a grid-barrier timeout (internal error)");
             // (the step enqueued ahead has replaced alpha0 on the device by its own: put this step's back -- it came home with
             // the read-back of the failed launch -- once the stream has run dry)
@@ -599,7 +606,7 @@ KK_API int kk_lanczos_expand(kk_op op, kk_basis b, int c0, int k, kk_orth_t orth
     *alpha = a;
     *beta = bt;
     if (npasses) *npasses = passes;
-    if (b->spec_valid) b->spec_beta = bt;  // the caller must come back with exactly this beta
+    if (b->ahead.valid) b->ahead.beta = bt;  // the caller must come back with exactly this beta
     return KK_OK;
 }
 
@@ -622,17 +629,13 @@ KK_API int kk_arnoldi_expand(kk_op op, kk_basis b, int c0, int k, kk_orth_t orth
     }
     const int la_sweeps = orth == KK_MGS ? 1 : (orth == KK_MGS2 ? 2 : 0);
     const bool strict_route = la_sweeps > 0 && m <= KK_MAX_M && !kk_mgs_lowsync(c, b->ld, m) && (!kk_sharded(c) || kk_xs_on(c));
-    // the previous call may have enqueued this WHOLE step already (apply, sweeps and read-back: la_enqueue)
-    const bool la_hit = b->la_valid && b->spec_valid && c->spec_owner == b && b->spec_gen == c->foreign_gen && b->spec_op == op && b->spec_c0 == c0 && b->spec_k == k &&
-                        b->spec_dot_mode == 0 && b->la_kind == 0 && b->la_k == k && b->la_nsweeps == la_sweeps && b->spec_beta == beta_old && strict_route && v_ready;
-    const int la_slot = b->la_slot;
-    const double la_token = b->la_token;
-    const bool inside_lost = la_hit && b->la_inside;   // the launch enqueued ahead was to form w = A v itself (taken now: la_enqueue below overwrites the flag)
+    // the previous call may have enqueued this WHOLE step already (apply, sweeps and read-back: la_enqueue; or the one launch)
+    const kk_ahead taken = b->ahead;   // (see kk_lanczos_expand)
+    const bool la_same = ahead_matches(b, op, c0, k, beta_old) && v_ready;
+    const bool la_hit = la_same && taken.dot_mode == 0 && taken.kind == kk_ahead_kind::sweep && taken.nsweeps == la_sweeps && strict_route;
     // the whole step in one launch (short vectors and short bases: kk_kernels_fstep.hip; round 6)
-    const bool fs_route = m <= KK_MAX_M && fstep_ok_arnoldi(c, op, b, c0, k, orth, la_sweeps > 0 && kk_mgs_lowsync(c, b->ld, m));
-    const bool la_fs_hit = b->la_valid && b->spec_valid && c->spec_owner == b && b->spec_gen == c->foreign_gen && b->spec_op == op && b->spec_c0 == c0 && b->spec_k == k &&
-                           b->la_kind == 2 && b->la_orth == 100 + (int)orth && b->la_k == k && b->spec_beta == beta_old && v_ready && fs_route;
-    if (b->la_valid && !la_hit && !la_fs_hit) b->spec_valid = false;   // the sweep enqueued ahead has consumed the speculative apply's column
+    const bool fs_route = m <= KK_MAX_M && fstep_ok(c, op, b, c0, k, orth, la_sweeps > 0 && kk_mgs_lowsync(c, b->ld, m), kk_solver::arnoldi);
+    const bool la_fs_hit = la_same && taken.kind == kk_ahead_kind::one_launch && taken.solver == kk_solver::arnoldi && taken.orth == orth && fs_route;
     bool hit = la_hit || la_fs_hit;
     if (!hit && !fs_route) KK_TRY(spec_take(op, b, c0, k, 0, beta_old, SCP(c, SC_ALPHA0), &hit));
     gram_touch(b, c0 + k);
@@ -641,34 +644,13 @@ KK_API int kk_arnoldi_expand(kk_op op, kk_basis b, int c0, int k, kk_orth_t orth
     else KK_TRY(kk_launch_scal(c, v, b->ld, 1.0 / beta_old, nullptr));  // push!(V, scale(r, 1/beta))   arnoldi.jl:209
     if (fs_route) {
         // w = A v, one or two orthogonalisation passes, the norm and the normalised commit in ONE launch; column of H and beta through the pinned slot
-        int slot = 2 + (k & 1);
-        double token = 0;
-        if (la_fs_hit) { slot = la_slot; token = la_token; }
-        else KK_TRY(fstep_enqueue(op, b, k, orth, nullptr, 0.0, 0, slot, &token, true));
-        b->spec_valid = false; b->la_valid = false;
-        if (c->lookahead && c->fold_scale && c0 + k + 3 <= b->cap && fstep_ok_arnoldi(c, op, b, c0, k + 1, orth, la_sweeps > 0 && kk_mgs_lowsync(c, b->ld, m + 1))) {
-            double tk = 0;
-            KK_TRY(fstep_enqueue(op, b, k + 1, orth, nullptr, 0.0, m, 2 + ((k + 1) & 1), &tk, true));
-            b->spec_valid = true; b->spec_op = op; b->spec_c0 = c0; b->spec_k = k + 1; b->spec_dot_mode = -1; b->spec_beta = 0.0; b->spec_dot_ptr = nullptr;
-            c->spec_owner = b; b->spec_gen = c->foreign_gen;
-            b->la_valid = true; b->la_k = k + 1; b->la_slot = 2 + ((k + 1) & 1); b->la_token = tk; b->la_nsweeps = 0; b->la_kind = 2; b->la_orth = 100 + (int)orth; b->la_rode = false;
-        }
-        if (!fstep_wait(c, slot, token)) {   // the launch gave up: route off for this context, the step again on the ordinary one (see kk_lanczos_expand)
-            KK_HIP(hipMemsetAsync((char*)c->d_fsync + KK_FS_SYNC_BYTES, 0, sizeof(int), c->stream));
-            ++c->fstep_failures;
-            c->fused_step = 0;
-            b->spec_valid = false; b->la_valid = false;
-            b->norm_col = c0 + k; b->norm_beta = beta_old;
-            return kk_arnoldi_expand(op, b, c0, k, orth, eta, beta_old, h, beta, npasses);
-        }
-        const double* hs = fstep_slot(c, slot);
+        const double* hs = nullptr;
+        KK_TRY(fstep_run(op, b, c0, k, orth, kk_solver::arnoldi, beta_old, la_sweeps > 0 && kk_mgs_lowsync(c, b->ld, m + 1), la_fs_hit ? &taken : nullptr, &hs));
+        if (!hs) return kk_arnoldi_expand(op, b, c0, k, orth, eta, beta_old, h, beta, npasses);
         for (int j = 0; j < m; ++j) h[j] = hs[8 + KK_FS_MAX_M + j];
         *beta = hs[4];
-        if (orth == KK_MGS || orth == KK_MGS2) lowsync_commit_row(b, m, hs + 8);
         if (npasses) *npasses = (orth == KK_CGS2 || orth == KK_MGS2) ? 2 : 1;
-        if (hs[6] != 0.0 && kk_persist_norm_applies(*beta)) { b->norm_col = c0 + k + 1; b->norm_beta = *beta; }
-        else { b->la_valid = false; b->spec_valid = false; }
-        if (b->spec_valid) b->spec_beta = *beta;
+        if (b->ahead.valid) b->ahead.beta = *beta;
         return KK_OK;
     }
     if (!hit) {
@@ -677,29 +659,24 @@ KK_API int kk_arnoldi_expand(kk_op op, kk_basis b, int c0, int k, kk_orth_t orth
     }
     if (la_hit) {
         // this step is in the stream (or done): enqueue the NEXT one behind it, then collect
-        KK_TRY(speculate_next(op, b, c0, k + 1, 0, false, 0.0, nullptr, la_apply_inside(op, b, c0, k + 1, la_sweeps)));
-        KK_TRY(la_enqueue(op, b, c0, k + 1, la_sweeps, false));
-        if (c->sweep_apply.on) {   // (la_enqueue declined after all: the apply as its own launch)
-            c->sweep_apply.on = false;
-            KK_TRY(speculate_next(op, b, c0, k + 1, 0, false, 0.0));
-        }
-        KK_HIP(hipEventSynchronize(c->ev_la[la_slot & 1]));
+        KK_TRY(enqueue_next(op, b, c0, k + 1, la_sweeps, kk_solver::arnoldi));
+        KK_HIP(hipEventSynchronize(c->ev_la[taken.slot & 1]));
         bool redo = false;
-        KK_TRY(persist_check_at(c, la_slot, la_token, &redo));
+        KK_TRY(persist_check_at(c, taken.slot, taken.token, &redo));
         if (!redo) {
-            for (int j = 0; j < m; ++j) h[j] = pin(c, WS_S, la_slot)[j] + (la_sweeps > 1 ? pin(c, WS_G, la_slot)[j] : 0.0);
-            *beta = pin(c, WS_SCAL + SC_NRM2, la_slot)[1];
+            for (int j = 0; j < m; ++j) h[j] = pin(c, WS_S, taken.slot)[j] + (la_sweeps > 1 ? pin(c, WS_G, taken.slot)[j] : 0.0);
+            *beta = pin(c, WS_SCAL + SC_NRM2, taken.slot)[1];
             if (npasses) *npasses = la_sweeps;
-            if (b->spec_valid) b->spec_beta = *beta;
+            if (b->ahead.valid) b->ahead.beta = *beta;
             if (kk_persist_norm_applies(*beta)) { b->norm_col = c0 + k + 1; b->norm_beta = *beta; }
             return KK_OK;
         }
         // grid-barrier timeout of the launch enqueued ahead: w = A v is untouched -- drop what was enqueued behind it and run
         // this step's sweeps on the ordinary route (which now takes the launch-per-vector kernels)
-        b->spec_valid = false; b->la_valid = false;
+        ahead_void(b);
         KK_TRY(stream_sync(c));
         c->persist_norm_done = false;
-        if (inside_lost) {   // ... unless the lost launch was to form A v itself (k_mgs_panel<.., APPLY>): then nothing has written w yet
+        if (taken.inside) {   // ... unless the lost launch was to form A v itself (k_mgs_panel<.., APPLY>): then nothing has written w yet
             kk_spmv_fuse f;
             KK_TRY(kk_launch_spmv(c, op->A, v, w, b->ld, f));
         }
@@ -713,7 +690,7 @@ KK_API int kk_arnoldi_expand(kk_op op, kk_basis b, int c0, int k, kk_orth_t orth
     c->persist_norm_req = false;
     c->spec_req.active = false;
     c->spec_req.la_nsweeps = 0;
-    if (st == KK_OK && b->spec_valid) b->spec_beta = *beta;
+    if (st == KK_OK && b->ahead.valid) b->ahead.beta = *beta;
     if (st == KK_OK && c->persist_norm_done && kk_persist_norm_applies(*beta)) { b->norm_col = c0 + k + 1; b->norm_beta = *beta; }
     return st;
 }

@@ -340,7 +340,7 @@ static int strict_sweeps_synced(kk_ctx c, const double* V, int64_t ld, int m, in
         KK_TRY(persist_check(c, &redo));
         if (!redo) return KK_OK;
         if (last_sync && req.active) {   // the speculative apply final_sync enqueued read a norm the failed launch never wrote
-            req.b->spec_valid = false;
+            ahead_void(req.b);
             c->spec_req = req;
         }
     }

@@ -104,19 +104,28 @@ def test_arnoldi_run_ahead_bitwise_and_gmres_counts(kk, ko, lctx, orth_name):
     ref = {"mgs": ko.MGS, "mgs2": ko.MGS2}[orth_name]
     C = ko.convection_diffusion_2d(48, 40)
     x0 = np.random.default_rng(8).random(C.shape[0])
-    out = {}
+    out, launches = {}, {}
+    sweeps = lambda: lctx.prof_get("k_mgs_persist")[1] + lctx.prof_get("k_mgs_panel")[1]
     for la in (1, 0):
         lctx.set_option("lookahead", la)
         it = kk.ArnoldiIterator(kk.SparseOperator(C, lctx), x0, dev, capacity=26)
         f = kk.initialize(it)
+        lctx.prof_reset(); lctx.prof_enable(1)
         for i in range(14):
             f = kk.expand_(it, f)
+        before_shrink = sweeps()
         f = kk.shrink_(f, 9)
         for i in range(8):
             f = kk.expand_(it, f)
+        lctx.prof_enable(0)
+        launches[la] = (before_shrink, sweeps() - before_shrink)
         out[la] = (np.array(f.H, dtype=float).copy(), f.V.to_numpy().copy(), f.r.get().copy())
     lctx.set_option("lookahead", 1)
     assert np.array_equal(out[1][0], out[0][0]) and np.array_equal(out[1][1], out[0][1])
+    # one sweep launch per step (MGS2: both sweeps in it); with the run-ahead every step finds the launch enqueued for it, and
+    # exactly one launch more goes out per stretch: the step the shrink! drops, and the one the last expand! enqueues
+    assert launches[0] == (14, 8), launches
+    assert launches[1] == (14 + 1, 8 + 1), launches
     oit = ko.ArnoldiIterator(C, x0.copy(), ref)
     of = ko.arnoldi_initialize(oit)
     for i in range(14):

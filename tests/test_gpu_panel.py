@@ -228,7 +228,7 @@ def test_panel_kernel_applies_the_stencil_itself(kk, ko, shape, orth_name):
 
 def test_lost_launch_that_was_to_apply_the_stencil_itself_is_repeated_with_its_apply(kk, ko):
     """a run-ahead launch of k_mgs_panel<.., APPLY> that gives up (test hook) has written nothing -- not even w = A v, which no other launch formed:
-    the recovery has to repeat the apply as well as the sweeps (kk_arnoldi_expand, `la_inside`)"""
+    the recovery has to repeat the apply as well as the sweeps (kk_arnoldi_expand, `kk_ahead::inside`)"""
     nx, ny = 600, 500
     A = ko.convection_diffusion_2d(nx, ny)
     x0 = np.random.default_rng(8).random(nx * ny)

@@ -1,6 +1,6 @@
 """Randomised interleavings of the C entry points against the oracle, with every piece of DEFERRED STATE of the slab switched
 on: the normalised residual column of the persistent kernels' commit (fold_scale -> norm_col), the speculative next apply
-(speculate -> spec_valid), the whole step enqueued ahead (lookahead -> la_valid), the cached Gram rows of the
+(speculate -> ahead.valid), the whole step enqueued ahead (lookahead -> ahead.kind), the cached Gram rows of the
 low-synchronisation form, and -- block factorizations -- the normalised block commit (block_commit -> tc_valid) with the cached
 Gram matrix of the residual block.  Each feature has its own tests; what none of them does is drive ARBITRARY sequences of
 entry points through all of them at once.  hypothesis draws the sequence; after every operation
