@@ -380,6 +380,15 @@ KK_API int kk_ctx_get_option(kk_ctx c, const char* key, double* value) {
     else if (!strcmp(key, "fstep_last_blocks")) *value = c->fstep_last_blocks;
     else if (!strcmp(key, "fstep_last_np")) *value = c->fstep_last_np;
     else if (!strcmp(key, "fstep_last_threads")) *value = c->fstep_last_threads;
+    else if (!strcmp(key, "sweep_last_kernel")) *value = c->sweep_last_kernel;
+    else if (!strcmp(key, "sweep_last_nv")) *value = c->sweep_last_nv;
+    else if (!strcmp(key, "sweep_last_nl")) *value = c->sweep_last_nl;
+    else if (!strcmp(key, "sweep_last_nr")) *value = c->sweep_last_nr;
+    else if (!strcmp(key, "sweep_last_p")) *value = c->sweep_last_p;
+    else if (!strcmp(key, "sweep_last_threads")) *value = c->sweep_last_threads;
+    else if (!strcmp(key, "sweep_last_nt")) *value = c->sweep_last_nt;
+    else if (!strcmp(key, "sweep_last_apply")) *value = c->sweep_last_apply;
+    else if (!strcmp(key, "sweep_last_blocks")) *value = c->sweep_last_blocks;
     else if (!strcmp(key, "spmv_dia_sw")) *value = c->spmv_dia_sw;
     else if (!strcmp(key, "spmv_dia_sw_lines")) *value = c->spmv_dia_sw_lines;
     else if (!strcmp(key, "spmv_dia_sw_launches")) *value = (double)c->spmv_dia_sw_launches;

@@ -250,6 +250,10 @@ struct kk_ctx_s {
     kk_sweep_apply sweep_apply;  // ... the pending request (see kk_sweep_apply)
     bool sweep_apply_fused = false;   // ... the last pass_mgs_strict_sweeps honoured one inside its launch (the work vector was never written by an apply of its own)
     int64_t panel_apply_launches = 0;   // diagnostics
+    // diagnostics: shape of the last persistent sweep launch (kk_launch_mgs_persist / kk_launch_mgs_panel; read-only options sweep_last_*):
+    // kernel 1 = k_mgs_persist, 2 = k_mgs_panel, 3 = k_mgs_panel_lag; template NV, NL, NR (persist only), P, NTPREV, APPLY; threads and blocks
+    int sweep_last_kernel = 0, sweep_last_nv = 0, sweep_last_nl = 0, sweep_last_nr = 0, sweep_last_p = 0, sweep_last_nt = 0, sweep_last_apply = 0;
+    int sweep_last_threads = 0, sweep_last_blocks = 0;
     int xsync = 1;               // row-sharded context: persistent kernels with the in-kernel cross-rank reduction where the communicator offers it (0: RCCL all-reduce per inner-product batch, low-sync route)
     int mgs_persist = 1;         // strict MGS sweeps through the persistent register-resident kernel when the vector fits
     int persist_coop = 0;        // launch the persistent kernels through hipLaunchCooperativeKernel (1) or as ordinary launches (0): see kk_launch_resident
@@ -615,6 +619,11 @@ int kk_launch_mgs_panel(kk_ctx ctx, const double* V, int64_t ld, int m, int nswe
                         const double* carry_s, double* out_s, int out_stride, double* nrm_out3, bool normalize_w, bool strict,
                         const kk_sweep_apply* apply = nullptr);
 bool kk_sweep_apply_ok(kk_ctx ctx, const kk_sparse_dev& M, int64_t ld);   // can the panel kernel apply this operator itself?
+// records the shape of a persistent sweep launch about to be made (options sweep_last_*)
+static inline void kk_sweep_note(kk_ctx ctx, int kernel, int nv, int nl, int nr, int p, int threads, bool nt, bool apply) {
+    ctx->sweep_last_kernel = kernel; ctx->sweep_last_nv = nv; ctx->sweep_last_nl = nl; ctx->sweep_last_nr = nr; ctx->sweep_last_p = p;
+    ctx->sweep_last_threads = threads; ctx->sweep_last_nt = nt ? 1 : 0; ctx->sweep_last_apply = apply ? 1 : 0; ctx->sweep_last_blocks = ctx->num_cus;
+}
 // does an MGS-family sweep over vectors of leading dimension ld run in the low-synchronisation (projection-based) form?
 // (option "mgs_mode").  auto: the persistent kernels wherever they are the faster route -- the panel kernel for vectors of
 // panel_min_rows .. 4.19 M rows, the register-resident strict kernel from persist_min_rows rows up to its capacity -- and the

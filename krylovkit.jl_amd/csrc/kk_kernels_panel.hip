@@ -758,6 +758,7 @@ bool kk_mgs_panel_eligible(kk_ctx ctx, int64_t ld_local) {
 
 template <int NV, int P>
 static int launch_panel_inst(kk_ctx ctx, void** args, bool apply = false) {
+    kk_sweep_note(ctx, 2, NV, 0, 0, P, KK_PANEL_PT, false, apply);
     if (apply) return kk_launch_resident(ctx, (const void*)k_mgs_panel<NV, P, true>, KK_PANEL_PT, args, 0, "k_mgs_panel");
     return kk_launch_resident(ctx, (const void*)k_mgs_panel<NV, P, false>, KK_PANEL_PT, args, 0, "k_mgs_panel");
 }
@@ -772,6 +773,7 @@ bool kk_sweep_apply_ok(kk_ctx ctx, const kk_sparse_dev& M, int64_t ld) {
 
 template <int NV, int P>
 static int launch_panel_lag_inst(kk_ctx ctx, void** args) {
+    kk_sweep_note(ctx, 3, NV, 0, 0, P, KK_PANEL_PT, false, false);
     return kk_launch_resident(ctx, (const void*)k_mgs_panel_lag<NV, P>, KK_PANEL_PT, args, 0, "k_mgs_panel_lag");
 }
 

@@ -504,6 +504,7 @@ static int launch_persist_inst2(kk_ctx ctx, void** args) {
         if (ea != hipSuccess) return kk_hip_fail(ea, "hipFuncSetAttribute(k_mgs_persist, MaxDynamicSharedMemorySize)", __FILE__, __LINE__);
         if (dev >= 0 && dev < KK_MAX_DEVICES) configured[dev] = true;
     }
+    kk_sweep_note(ctx, 1, NV, NL, NR, 1, PT, NT, APPLY);
     return kk_launch_resident(ctx, fn, PT, args, dyn, "k_mgs_persist");
 }
 // grid-rows of the current basis vector kept in spare registers on top of the LDS-parked ones: only where the work vector

@@ -12,14 +12,9 @@ import numpy as np
 import pytest
 
 import xprec_step as xp
+from xprec_step import check_step, one_step, orth as _orth
 
 pytestmark = pytest.mark.gpu
-
-ORTHS = {"cgs": "ClassicalGramSchmidt", "mgs": "ModifiedGramSchmidt", "cgs2": "ClassicalGramSchmidt2", "mgs2": "ModifiedGramSchmidt2"}
-
-
-def _orth(kk, name):
-    return getattr(kk, ORTHS[name])()
 
 
 def _context(kk, threads, blocks):
@@ -29,56 +24,6 @@ def _context(kk, threads, blocks):
     c.set_option("mgs_mode", 1)       # (MGS in its low-synchronisation form at every length: the form the one launch carries)
     c.set_option("lookahead", 0)      # (one step: nothing enqueued behind it)
     return c
-
-
-def one_step(kk, c, op, A, V, beta_old, kind, orth):
-    """upload V with r = beta_old v in column m - 1, one expand! with k = m - 1; returns the device's results and its f64 inputs as read back"""
-    n, m = V.shape
-    lib = c._lib
-    B = kk.DeviceBasis(n, m + 2, c)
-    for j in range(m - 1):
-        B.upload(j, V[:, j])
-    B.upload(m - 1, beta_old * V[:, m - 1])
-    o = _orth(kk, orth)
-    b, npass = C.c_double(), C.c_int()
-    if kind == "lanczos":
-        a = C.c_double()
-        kk._lib.check(lib.kk_lanczos_expand(op.handle, B.handle, 0, m - 1, o.code, o.eta, beta_old, C.byref(a), C.byref(b), C.byref(npass)))
-        out = {"alpha": a.value}
-    else:
-        h = np.zeros(m)
-        kk._lib.check(lib.kk_arnoldi_expand(op.handle, B.handle, 0, m - 1, o.code, o.eta, beta_old, h.ctypes.data_as(kk._lib.c_dp), C.byref(b),
-                                            C.byref(npass)))
-        out = {"h": h}
-    out["beta"] = b.value
-    Vd = np.stack([B.download(j) for j in range(m)], axis=1)     # the device's inputs: column m - 1 = v as normalised in the stream
-    out["r"] = B.download(m)      # (a column stored normalised is handed out times beta: an error in the stored column shows here)
-    if orth.startswith("mgs"):
-        # the Gram row the host took (row m - 1 of the slab's cached rows) through an operation that must use it: MGS of a probe vector
-        # against columns 0 .. m - 1 with the solve on the host's rows (low-sync, unfused)
-        x = np.random.default_rng(m).standard_normal(n)
-        B.upload(m + 1, x)
-        c.set_option("fuse_passes", 0)
-        out["probe"] = (x, B.orthogonalize(kk.HipVec(B, m + 1), kk.ModifiedGramSchmidt(), 0, m, want_norm=False)[0])
-        c.set_option("fuse_passes", 1)
-    B.free()
-    return out, Vd
-
-
-def check_step(out, Vd, A, beta_old, kind, orth, width):
-    n, m = Vd.shape
-    op = xp.coo(A)
-    ref = xp.lanczos_step(op, Vd, beta_old, orth) if kind == "lanczos" else xp.arnoldi_step(op, Vd, orth)
-    key = "alpha" if kind == "lanczos" else "h"
-    errs = {key: xp.excess(out[key], getattr(ref, key), ref.scale[key], m, width, n),
-            "beta": xp.excess(out["beta"], ref.beta, ref.scale["beta"], m, width, n),
-            "r": xp.excess(out["r"], ref.r, ref.scale["r"], m, width, n),
-            "q": xp.excess(out["r"] / out["beta"], ref.q, ref.scale["q"], m, width, n)}
-    if "probe" in out:
-        x, s = out["probe"]
-        s_ref, s_scale = xp.mgs_coefficients(Vd, x)
-        errs["gram"] = xp.excess(s, s_ref, s_scale, m, 0, n)
-    return errs
 
 
 def _cases():

@@ -39,6 +39,7 @@ The errors the test must catch (the four variants above) are larger by many orde
 `skewed_basis` (test_xprec_step.py::test_bound_discriminates)."""
 from __future__ import annotations
 
+import ctypes as C
 import math
 from dataclasses import dataclass, field
 from typing import Dict, Optional
@@ -406,3 +407,64 @@ def envelope_inputs(shape_index: int, case_index: int):
     V = skewed_basis(nx * ny, m, seed)
     beta_old = 0.75 + 0.5 * np.random.default_rng(seed).random()
     return A, V, beta_old
+
+
+# ---- one expand! through the C ABI and its check (tests/test_gpu_fstep_envelope.py, tests/test_gpu_sweep_envelope.py) --------------
+ORTHS = {"cgs": "ClassicalGramSchmidt", "mgs": "ModifiedGramSchmidt", "cgs2": "ClassicalGramSchmidt2", "mgs2": "ModifiedGramSchmidt2"}
+
+
+def orth(kk, name):
+    return getattr(kk, ORTHS[name])()
+
+
+def one_step(kk, c, op, A, V, beta_old, kind, orth_name, on_step=None):
+    """upload V with r = beta_old v in column m - 1, one expand! with k = m - 1; returns the device's results and its f64 inputs as read back
+    (`on_step()`: called right behind the expand!, before anything else is launched)"""
+    n, m = V.shape
+    lib = c._lib
+    B = kk.DeviceBasis(n, m + 2, c)
+    for j in range(m - 1):
+        B.upload(j, V[:, j])
+    B.upload(m - 1, beta_old * V[:, m - 1])
+    o = orth(kk, orth_name)
+    b, npass = C.c_double(), C.c_int()
+    if kind == "lanczos":
+        a = C.c_double()
+        kk._lib.check(lib.kk_lanczos_expand(op.handle, B.handle, 0, m - 1, o.code, o.eta, beta_old, C.byref(a), C.byref(b), C.byref(npass)))
+        out = {"alpha": a.value}
+    else:
+        h = np.zeros(m)
+        kk._lib.check(lib.kk_arnoldi_expand(op.handle, B.handle, 0, m - 1, o.code, o.eta, beta_old, h.ctypes.data_as(kk._lib.c_dp), C.byref(b),
+                                            C.byref(npass)))
+        out = {"h": h}
+    if on_step is not None:
+        on_step()
+    out["beta"] = b.value
+    Vd = np.stack([B.download(j) for j in range(m)], axis=1)     # the device's inputs: column m - 1 = v as normalised in the stream
+    out["r"] = B.download(m)      # (a column stored normalised is handed out times beta: an error in the stored column shows here)
+    if orth_name.startswith("mgs"):
+        # the Gram row the host took (row m - 1 of the slab's cached rows) through an operation that must use it: MGS of a probe vector
+        # against columns 0 .. m - 1 with the solve on the host's rows (low-sync, unfused)
+        x = np.random.default_rng(m).standard_normal(n)
+        B.upload(m + 1, x)
+        c.set_option("fuse_passes", 0)
+        out["probe"] = (x, B.orthogonalize(kk.HipVec(B, m + 1), kk.ModifiedGramSchmidt(), 0, m, want_norm=False)[0])
+        c.set_option("fuse_passes", 1)
+    B.free()
+    return out, Vd
+
+
+def check_step(out, Vd, A, beta_old, kind, orth, width):
+    n, m = Vd.shape
+    op = coo(A)
+    ref = lanczos_step(op, Vd, beta_old, orth) if kind == "lanczos" else arnoldi_step(op, Vd, orth)
+    key = "alpha" if kind == "lanczos" else "h"
+    errs = {key: excess(out[key], getattr(ref, key), ref.scale[key], m, width, n),
+            "beta": excess(out["beta"], ref.beta, ref.scale["beta"], m, width, n),
+            "r": excess(out["r"], ref.r, ref.scale["r"], m, width, n),
+            "q": excess(out["r"] / out["beta"], ref.q, ref.scale["q"], m, width, n)}
+    if "probe" in out:
+        x, s = out["probe"]
+        s_ref, s_scale = mgs_coefficients(Vd, x)
+        errs["gram"] = excess(s, s_ref, s_scale, m, 0, n)
+    return errs
